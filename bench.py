@@ -4,7 +4,7 @@
 BASELINE.json metric: "Encode GiB/s device-resident ((k+m)*vec/cost),
 10+4 @1MiB, 1/2/4/8 GPU; %HBM peak".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one launch of the HIP encode over one batch of S synthetic stripes
@@ -20,17 +20,27 @@ in to RCCL; the line's `backend` and `rank_devices` say which ran).
 as a child process, before any GPU call); under a launcher WORLD_SIZE must
 equal N and every rank must join, or the run exits non-zero (`ranks_seen`).
 
-Order per rank: self-check (encode -> erase -> reconst), pre-warm until the
-launch time has settled (at least 250 launches; 20 consecutive within 3 %
-and within 0.5 % of the 20 before; `prewarm` in the line), W counted
-warm-up steps queued right behind it, K timed steps; then (`cold`) 50
-launches after a 100 ms idle, the rate a bursty caller sees.
+A plain run does what the headline needs and no more.  Order per rank:
+pre-warm until the launch time has settled (at least 250 launches; 20
+consecutive within 3 % and within 0.5 % of the 20 before; `prewarm` in the
+line), W counted warm-up steps queued right behind it, K timed steps, then
+`--dump-outputs DIR` if given: the parity the last timed step wrote, as
+DIR/parity_sample.npy (float32: a fixed, seeded sample of rows and columns,
+dump_sample) and DIR/parity_rowsum.npy (float64: the byte sum of every
+parity vector).  The stripes are seeded, so two builds run with the same
+arguments can be compared file for file.
+
+`--full` adds everything else the line can carry: the self-check (encode ->
+erase -> reconst) before the pre-warm; behind the timed steps a per-launch
+spread pass (`timed_spread`), 50 launches after a 100 ms idle (`cold`, the
+rate a bursty caller sees) and the host-resident legs (`end_to_end`); and
+`cpu_baseline`, the oracle's AVX2 restatement of the reference's
+split-nibble path on the host's cores over a bounded sample.
 
 Rank 0 prints ONE JSON line.  `value` = (k+m)*vec*S*N*K / max-rank time in
 GiB/s.  `roofline` prices the encode kernel itself: algorithmic bytes per
-launch / mean launch time from HIP events on the launch stream, against
-8 TB/s HBM3E.  `cpu_baseline` times the oracle's AVX2 restatement of the
-reference's split-nibble path on one host core over a bounded sample.
+launch / mean launch time from the HIP event pair around the timed steps,
+against 8 TB/s HBM3E.
 """
 from __future__ import annotations
 
@@ -66,16 +76,25 @@ def parse_args(argv=None):
     ap.add_argument("--layout", default=os.environ.get("RSAMD_BENCH_LAYOUT", "split"), choices=("split", "interleaved"),
                     help="split: data [S][k][vec] and parity [S][m][vec] in separate buffers; "
                          "interleaved: one [S][k+m][vec] buffer")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU-baseline sample (0 = skip)")
-    ap.add_argument("--verify", type=int, default=1, help="encode->erase->reconst self-check of one stripe per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: self-check, per-launch spread pass, cold "
+                         "launches, host-resident end-to-end legs, CPU baseline (each still subject to its own "
+                         "switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the parity of the last timed step to DIR as .npy "
+                         "(parity_sample: float32 seeded sample; parity_rowsum: float64 byte sums)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0,
+                    help="--full: bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--verify", type=int, default=1,
+                    help="--full: encode->erase->reconst self-check of one stripe per rank")
     ap.add_argument("--e2e-stripes", type=int, default=128,
-                    help="stripes per GPU for the host-resident end-to-end leg (0 = skip)")
+                    help="--full: stripes per GPU for the host-resident end-to-end leg (0 = skip)")
     ap.add_argument("--e2e-reps", type=int, default=10)
     ap.add_argument("--prewarm-min", type=int, default=250,
                     help="pre-warm: at least this many launches before the counted warm-up")
     ap.add_argument("--prewarm-max", type=int, default=2000, help="pre-warm: at most this many launches")
     ap.add_argument("--cold", type=int, default=1,
-                    help="after the timed region: 50 launches after a 100 ms idle (`cold` in the line)")
+                    help="--full: after the timed region, 50 launches after a 100 ms idle (`cold` in the line)")
     ap.add_argument("--group", type=int, default=0,
                     help="one process drives N device-resident codecs through a device group "
                          "(rs_group_codec; the topology of a Go storage server), instead of one rank per GPU; "
@@ -83,7 +102,10 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="TEST ONLY: rehearse the launcher / rank / timing protocol on CPU (gloo, no GPU, "
                          "no kernel); the line it prints is not a measurement")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs K >= 1 and --warmup W >= 0")
+    return args
 
 
 # ---------------------------------------------------------------- distributed plumbing
@@ -352,6 +374,62 @@ def load_traffic(config: str, algorithmic_bytes: int):
         return b, f"profiles/traffic.json <- {ent.get('source')}"
     except (OSError, ValueError, ZeroDivisionError):
         return None, None
+
+
+# ---------------------------------------------------------------- outputs
+
+DUMP_ELEMS = 8 << 20  # sampled parity bytes: 32 MiB as float32 (the dump stays under 64 MB)
+DUMP_ROWS = 4096      # at most this many parity vectors in the sample
+DUMP_SEED = 0x0D5EED
+
+
+def dump_sample(rows: int, vec: int, elems: int = DUMP_ELEMS, max_rows: int = DUMP_ROWS, seed: int = DUMP_SEED):
+    """Which bytes of `rows` parity vectors of `vec` bytes --dump-outputs
+    keeps: (row indices, column indices), sorted int64, the same for every run
+    of a shape.  Everything when it fits in `elems`; otherwise at most
+    `max_rows` vectors (the first and the last among them) and as many
+    columns of each as the budget allows (the first and last 64 among them,
+    where a tail or alignment defect would sit)."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+
+    def pick(n, want, edge):
+        if want >= n:
+            return np.arange(n, dtype=np.int64)
+        ends = np.concatenate([np.arange(edge), np.arange(n - edge, n)])
+        inner = rng.choice(n, max(want - 2 * edge, 0), replace=False)
+        return np.unique(np.concatenate([ends, inner]).astype(np.int64))
+
+    if rows * vec <= elems:
+        return np.arange(rows, dtype=np.int64), np.arange(vec, dtype=np.int64)
+    r = pick(rows, max_rows, 1)
+    return r, pick(vec, elems // len(r), 64)
+
+
+def dump_outputs(dirpath: str, parity, rank: int = 0, world: int = 1) -> dict:
+    """Write what a caller of the timed path holds after its last step, the
+    parity tensor [S][m][vec], as .npy: a float32 sample (dump_sample over the
+    S*m vectors) and the float64 byte sum of every vector (exact: vec * 255
+    is far below 2**53), which moves when any byte outside the sample does."""
+    import numpy as np
+    import torch
+
+    S, m, vec = parity.shape
+    r, c = dump_sample(S * m, vec)
+    ri = torch.from_numpy(r).to(parity.device)
+    ci = torch.from_numpy(c).to(parity.device)
+    sample = parity[(ri // m)[:, None], (ri % m)[:, None], ci[None, :]]
+    rowsum = parity.sum(dim=2, dtype=torch.int64)
+    os.makedirs(dirpath, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    files = {f"parity_sample{tag}": sample.cpu().numpy().astype(np.float32),
+             f"parity_rowsum{tag}": rowsum.cpu().numpy().astype(np.float64)}
+    for name, arr in files.items():
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
+    return {"dir": dirpath, "files": {n: [str(a.dtype), list(a.shape)] for n, a in files.items()},
+            "rule": "parity [S][m][vec] after the last timed step; sample = dump_sample rows (of the S*m "
+                    "vectors) x columns, rowsum = byte sum of every vector"}
 
 
 # ---------------------------------------------------------------- launcher
@@ -742,6 +820,8 @@ def main(argv=None):
     if args.group:
         if launched or args.gpus != 1:
             raise SystemExit("bench: --group N runs in one process (no launcher, no --gpus)")
+        if args.dump_outputs:
+            raise SystemExit("bench: --dump-outputs writes the rank path's parity; not available with --group")
         return group_main(args)
     if not launched and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus, raw))
@@ -810,7 +890,7 @@ def main(argv=None):
         def step(_i):
             codec.encode_batch_split(data, parity, stream=stream)
 
-    if args.verify:
+    if args.full and args.verify:
         # Self-check without the oracle (bench must not run it outside the
         # CPU-baseline leg): encode, erase 4 vectors of one stripe, rebuild,
         # compare.  Done before the warm-up so no idle gap separates the
@@ -866,11 +946,15 @@ def main(argv=None):
 
     bytes_per_step_rank = S * (k + m) * vec
     value = throughput(bytes_per_step_rank, n_gpus, args.steps, elapsed)
-    after = spread(launch_spread(step, stream, max(args.steps, 20)))
-    cold = cold_launches(step, stream, bytes_per_step_rank, max_over) if args.cold else None
+    # the last timed step's parity, before any later leg launches the step again
+    dumped = dump_outputs(args.dump_outputs, parity, rank, world) if args.dump_outputs else None
+
+    # everything below the timed region runs with --full only
+    after = spread(launch_spread(step, stream, max(args.steps, 20))) if args.full else None
+    cold = cold_launches(step, stream, bytes_per_step_rank, max_over) if args.full and args.cold else None
 
     e2e = None
-    if args.e2e_stripes > 0:
+    if args.full and args.e2e_stripes > 0:
         e2e = end_to_end(codec, data, parity, k, m, vec, min(args.e2e_stripes, S), args.e2e_reps, n_gpus,
                          barrier, max_over, lambda: torch.cuda.synchronize(dev))
     achieved = bytes_per_step_rank / kern_mean_s / 1e9
@@ -917,14 +1001,16 @@ def main(argv=None):
                 "kernel_timing": "HIP event pair on the launch stream around the K timed launches / K",
             },
             "prewarm": prewarm_summary(pw_n, pw_ms, pw_mean, pw_ok, pw_durs, args.prewarm_min),
-            "timed_spread": dict(after or {}, rule="rank 0: per-launch HIP-event times of max(K, 20) launches "
+            "timed_spread": dict(after, rule="rank 0: per-launch HIP-event times of max(K, 20) launches "
                                  "queued right behind the timed region (same steady state; the timed window "
-                                 "itself has one event pair, no per-launch events)"),
+                                 "itself has one event pair, no per-launch events)") if after else None,
+            "full": args.full,
+            "outputs": dumped,
         }
         result["cold"] = cold
         result["end_to_end"] = e2e
         result["build"] = rs.build_info()
-        if n_gpus == 1 and args.cpu_seconds > 0:
+        if args.full and n_gpus == 1 and args.cpu_seconds > 0:
             result["cpu_baseline"] = cpu_baseline(k, m, vec, args.cpu_seconds)
         else:
             result["cpu_baseline"] = None

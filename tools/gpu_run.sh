@@ -8,7 +8,7 @@
 #   tools/gpu_run.sh smoke
 #   tools/gpu_run.sh "tests:tests/test_gpu_tune_sweep.py"      # pytest -m gpu on those paths
 #   tools/gpu_run.sh tests                                      # every GPU test
-#   tools/gpu_run.sh bench "bench:--config 12+4@1MiB"           # bench.py (driver's command + extra args)
+#   tools/gpu_run.sh bench "bench:--config 12+4@1MiB"           # bench.py --full (driver's command, every leg, + extra args)
 #   tools/gpu_run.sh "ops:--only wide"                          # tools/ops_bench.py with args
 #   tools/gpu_run.sh "ab:AB_K=16,AB_M=16:op=rec16,jit=0:op=rec16,jit=2"   # tools/ab.py: env, then specs
 #   tools/gpu_run.sh "py:tools/some_probe.py args"              # any python script
@@ -44,7 +44,7 @@ for step in "$@"; do
       tail -3 "$log" ;;
     bench)
       # shellcheck disable=SC2086
-      timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 $arg > "$log" 2>&1 || fail "$step" $? "$log"
+      timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full $arg > "$log" 2>&1 || fail "$step" $? "$log"
       grep '^{' "$log" | cut -c1-400 ;;
     ops)
       # shellcheck disable=SC2086

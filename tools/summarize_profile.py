@@ -79,7 +79,7 @@ summary = {
     "launches_traced": len(durs),
     "duration_ns_mean_all_launches": statistics.mean(durs) if durs else None,
     "duration_ns_mean_timed_region": statistics.mean(durs[-steps:]) if durs else None,
-    "timed_region_note": f"last {steps} launches = bench.py's timed steps (the earlier ones are the self-check "
+    "timed_region_note": f"last {steps} launches = bench.py's timed steps (the earlier ones are the pre-warm "
                          "and warm-up, which include the post-idle power transient)",
     "FETCH_SIZE_KiB_median": statistics.median(fetch),
     "WRITE_SIZE_KiB_median": statistics.median(write),
